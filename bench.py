@@ -18,7 +18,15 @@ MPI_Reduce, main.c:656).  value = bits scanned by all ranks / wall time of the K
 N > 1 is weak scaling: every rank holds its own 1 GiB byte range (+ m-1 halo) of one N GiB text
 (shard formula main.c:467-477); there is no data-path collective.
 
-Extra objects on the JSON line (every one of them at every N unless it says otherwise):
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line (`value`,
+`ms_per_step` = wall milliseconds of one timed step, `roofline` from the timed steps' events).  `--full` adds everything
+below (side configurations, verification, CPU baselines, the idle-start rerun, the one-process leg); the `--no-*` options
+trim a --full run.  `--dump-outputs DIR` writes what the last timed step computed -- the three all-reduced 64-bit counts,
+m = 8 / 16 / 32 -- as DIR/ac_counts.npy (float64, exact below 2^53); text and patterns are seeded, so two builds run with
+the same arguments can be compared count for count.
+
+Extra objects on the JSON line (`roofline` and `ac` on every run, the others with --full; every one of them at every N unless
+it says otherwise):
   roofline               HBM bound; achieved = algorithmic bytes per launch (1 byte per text symbol) / mean
                          launch duration from events on the launch stream; traffic from the committed
                          rocprofv3 --pmc passes when they were taken on THIS build of the kernels
@@ -726,17 +734,20 @@ def phase_headline(R):
     elapsed = time.perf_counter() - t0
     counts = step_counts[args.warmup + args.steps - 1] if args.steps else step_counts[0]
     elapsed = max(sharded.gather_objects(elapsed))  # the job's time is the slowest rank's
-    # for the record: the same W + K steps started on an IDLE device, i.e. what this file measured before it conditioned
-    # the device (the transient of `conditioned` falls into the timed steps)
-    time.sleep(0.3)
-    base = args.warmup + args.steps
-    sharded.finish([step(base + k) for k in range(args.warmup)])
-    R.barrier()
-    t0 = time.perf_counter()
-    sharded.finish([step(base + args.warmup + k) for k in range(args.steps)])
-    R.barrier()
-    idle_elapsed = max(sharded.gather_objects(time.perf_counter() - t0))
     total_counts = [int(x) for x in counts.tolist()]
+    R.last_step_counts = total_counts
+    idle_elapsed = None
+    if args.full:
+        # for the record: the same W + K steps started on an IDLE device, i.e. what this file measured before it conditioned
+        # the device (the transient of `conditioned` falls into the timed steps)
+        time.sleep(0.3)
+        base = args.warmup + args.steps
+        sharded.finish([step(base + k) for k in range(args.warmup)])
+        R.barrier()
+        t0 = time.perf_counter()
+        sharded.finish([step(base + args.warmup + k) for k in range(args.steps)])
+        R.barrier()
+        idle_elapsed = max(sharded.gather_objects(time.perf_counter() - t0))
     # per-GPU counts for the report: one untimed pass without the reduce, then one small all-gather
     counts = step_counts[-1]
     counts.zero_()
@@ -794,17 +805,18 @@ def phase_headline(R):
                                "step = 3 scans + count all-reduce" % (args.mib_per_gpu, AC_PATTERNS),
                    "text_bytes_per_gpu": R.per_gpu, "alphabet": SIGMA, "patterns": AC_PATTERNS,
                    "pattern_lengths": list(AC_LENGTHS), "text_seed": TEXT_SEED, "pattern_seed": PAT_SEED,
-                   "sharding": sharding_label(R.world, R.backend, args.share_device)},
+                   "sharding": sharding_label(R.world, R.backend, args.share_device), "full": bool(args.full)},
         # who ran (round 6): the backend and world size as torch.distributed reports them, one identity per rank, distinct cards
         "world": dict(world_size=R.dist.get_world_size() if R.world > 1 else 1, backend=R.backend or "none", distinct_cards=n_cards,
                       rehearsal=bool(args.share_device), ranks=ranks),
-        "after_idle": {"what": "the same %d warm-up + %d timed steps started on an idle device, without the conditioning: the "
-                               "power-management transient falls into the timed steps" % (args.warmup, args.steps),
-                       "ms_per_step": round(idle_elapsed / max(args.steps, 1) * 1e3, 4),
-                       "value": round(bits_per_step * args.steps / idle_elapsed / 1e9, 2) if args.steps else None},
         "roofline": roofline, "ac": ac_detail, "device": S.device_name(), "kernel_build_id": kernel_build_id(),
         "per_gpu_matches": {"m%d" % m: [int(r[i]) for r in per_gpu_counts] for i, m in enumerate(AC_LENGTHS)},
     }
+    if idle_elapsed is not None:
+        R.out["after_idle"] = {"what": "the same %d warm-up + %d timed steps started on an idle device, without the conditioning: the "
+                                       "power-management transient falls into the timed steps" % (args.warmup, args.steps),
+                               "ms_per_step": round(idle_elapsed / max(args.steps, 1) * 1e3, 4),
+                               "value": round(bits_per_step * args.steps / idle_elapsed / 1e9, 2) if args.steps else None}
     if args.share_device:
         R.out["rehearsal"] = "--share-device: every rank on device 0, process group over gloo; rates are not N-GPU rates"
 
@@ -1405,11 +1417,20 @@ def phase_cpu_baselines(R):
         R.parity_ok = R.parity_ok and ok
 
 
+def dump_outputs(R, path):
+    """rank 0: what the last timed step computed -> DIR/ac_counts.npy (the all-reduced counts of the m = 8 / 16 / 32 sets, float64)"""
+    if R.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    R.np.save(os.path.join(path, "ac_counts.npy"), R.np.asarray(R.last_step_counts, dtype=R.np.float64))
+
+
 def finish(R):
     """rank 0: the record out (compact line LAST on stdout, full record to bench_detail.json); every rank: the process group down"""
     if R.rank == 0:
-        R.out["parity_ok"] = bool(R.parity_ok)
-        R.out["smh_multi_ok"] = R.multi_ok
+        if R.args.full:  # a plain run checks nothing beyond the timed path: it claims no parity
+            R.out["parity_ok"] = bool(R.parity_ok)
+            R.out["smh_multi_ok"] = R.multi_ok
         R.out["wall_s"] = round(time.perf_counter() - R.wall_t0, 1)
         R.out["phases_s"] = R.phases
         emit(R.out)
@@ -1442,6 +1463,10 @@ def main():
     ap.add_argument("--shard-mib", type=int, default=4096, help="per-GPU shard of the 32 GB configurations (configs[3], [4])")
     ap.add_argument("--verify-mib", type=int, default=-1,
                     help="MiB of every 4 GiB shard the CPU recounts (head + last 64 MiB); 0 = all of it; default: all at N = 1; at N > 1 8 MiB per host thread of the rank, 128..512")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: side configurations, verification, CPU baselines, idle-start rerun, one-process leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's counts to DIR/ac_counts.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines and the verification")
     ap.add_argument("--no-wm", action="store_true", help="skip the side configurations (WM, configs[3], configs[4])")
     ap.add_argument("--no-multi", action="store_true", help="skip the one-process smh_multi leg")
@@ -1460,6 +1485,11 @@ def main():
 
     R = Run(args)
     phase_headline(R)
+    if args.dump_outputs:
+        dump_outputs(R, args.dump_outputs)
+    if not args.full:
+        finish(R)
+        return
     phase_stream_read_and_positions(R)
     if not args.no_wm:
         phase_wm_and_automaton(R)

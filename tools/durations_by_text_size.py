@@ -19,7 +19,7 @@ def main():
             name = r["Kernel_Name"].split("(")[0].replace("void ", "").strip()
             if any(k in name for k in KEEP):
                 d.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    print("per-dispatch durations from the kernel trace of `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu`,")
+    print("per-dispatch durations from the kernel trace of `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu`,")
     print("grouped where one kernel instance served launches over different text sizes (1 GiB headline sets, 4 GiB shards)\n")
     for name, v in d.items():
         groups, cur = [], []

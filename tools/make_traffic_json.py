@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """profiles/hbm_traffic.json from two rocprofv3 counter passes (MI355X_MICROARCH.md, HBM section):
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d FETCH_DIR -- python3 bench.py --steps 3 --warmup 1 --no-cpu
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d WRITE_DIR -- python3 bench.py --steps 3 --warmup 1 --no-cpu
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d FETCH_DIR -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d WRITE_DIR -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu
     python tools/make_traffic_json.py FETCH_DIR WRITE_DIR > profiles/rNN/hbm_traffic.json
 
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE counts a 128-byte request as 64 bytes, so the
@@ -65,7 +65,7 @@ def main():
         if len(groups) > 1:
             out[name]["by_text_size"] = [dict(dispatches=len(g), hbm_read_bytes=int(round(sum(g) / len(g) * 1024 * 2))) for g in groups]
     json.dump(dict(build_id=kernel_build_id(), profile=sys.argv[3] if len(sys.argv) > 3 else "",
-                   source="rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 "
+                   source="rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 "
                           "--warmup 1 --no-cpu; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts 128-B requests "
                           "as 64 B); AC and wm_pair kernels of the headline sets scan 1 GiB per launch, the configs[3] / configs[4] "
                           "instances the shard size bench.py reports",
